@@ -2,6 +2,7 @@
 """Headline benchmark: images/sec (fwd+bwd+optimizer) of the DSF training hot path on MI355X.
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py ... --dump-outputs DIR                  (deterministic kernels; the last timed step's outputs as DIR/<name>.npy)
 
 Workload (BASELINE.json configs[1]): per-GPU batch 32, ResNet-18 two-stage backbone
 (``MANO_OCR_stage('ResNet_stage_18', 21, refine=True)``, reference config.py:38,80,93) + MANO layer +
@@ -640,6 +641,41 @@ def build_workload(args, dev, rank, world):
     return w
 
 
+DUMP_SAMPLE = 4 << 20          # --dump-outputs: elements kept of a larger flattened array (16 MB of float32)
+
+
+def dump_outputs(path, loss, terms, net, prefix="", params=True):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, its terms, and the network it updated (parameters,
+    their gradients, floating-point buffers such as BatchNorm running statistics, each flattened in module order) -- as
+    ``path/<prefix><name>.npy`` in float32 / float64.  An array of more than DUMP_SAMPLE elements is cut to a fixed sample
+    (seed 0, positions ascending), so that the files of two builds line up element for element; under 64 MB in all."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, t):
+        t = torch.as_tensor(t).detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+    def flat_sample(ts):
+        x = torch.cat([t.detach().reshape(-1).float() for t in ts])
+        if x.numel() <= DUMP_SAMPLE:
+            return x
+        idx = np.sort(np.random.default_rng(0).choice(x.numel(), DUMP_SAMPLE, replace=False))
+        return x[torch.from_numpy(idx).to(x.device)]
+
+    save(prefix + "loss", loss)
+    for k, v in terms.items():
+        save(prefix + "term_" + k, v)
+    plist = list(net.parameters())
+    if params:
+        save(prefix + "params", flat_sample(plist))
+    save(prefix + "grads", flat_sample([p.grad if p.grad is not None else torch.zeros_like(p) for p in plist]))
+    bufs = [b for b in net.buffers() if b.is_floating_point()]
+    if bufs:
+        save(prefix + "buffers", flat_sample(bufs))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -660,7 +696,17 @@ def main():
                     "single GPU): same kernels, no host issue -- pays below batch 16, where the step is host-bound")
     ap.add_argument("--no-graph", action="store_true", help="config 3 only: the eager step instead of its default HIP-graph replay")
     ap.add_argument("--cpu-steps", type=int, default=0, help="steps of the CPU baseline leg (0: sized per config to ~10-30 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one returned (loss, loss terms) and a fixed sample of the network "
+                         "it updated (parameters, gradients, buffers) as DIR/<name>.npy, to compare two builds output for output.  "
+                         "The run times and dumps the library's deterministic kernels (DSF_DETERMINISTIC=1; the result line says "
+                         "so): the default kernels add with float atomics, and AdamW's sign-like early updates turn those last-bit "
+                         "differences of near-zero gradients into +-lr weight changes, so two default runs part far beyond "
+                         "rounding.  Configs 2 and 3 also write default_*.npy: one forward + backward of the DEFAULT kernels from "
+                         "the state the timed steps left (same inputs, no optimizer step), reproducible to rounding")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks as CHILD processes (one per GPU) before this
@@ -684,6 +730,14 @@ def main():
     torch.backends.cudnn.benchmark = os.environ.get("DSF_MIOPEN_FIND", "0") == "1"   # reference :87 uses find mode; gfx950 ships no MIOpen find-db, find mode JIT-compiles every solver (hours)
 
     PMC_CONFIG[0] = args.config
+    from dsf_amd import _lib
+    from dsf_amd.train_step import GRAPH_ONE_STREAM
+    default_mode = _lib.deterministic()
+    if args.dump_outputs:
+        # the default kernels accumulate with float atomics: two runs differ in the last bits of every step, and AdamW's sign-like
+        # early updates turn that into +-lr weight changes wherever a gradient is near zero -- two runs' trajectories part far past
+        # rounding.  The bit-reproducible kernels run the same step (see --dump-outputs; default_*.npy covers the default kernels).
+        _lib.set_deterministic(True)
     w = build_workload(args, dev, rank, world)
     step, run = w["step"], w["run"]
     # config 3 is host-bound in eager mode (1,400+ launches of 10-60 us kernels per step): its default is the HIP-graph replay
@@ -708,7 +762,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            loss, _ = run()
+            loss, terms = run()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -718,6 +772,16 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     loss_val = float(loss)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, terms, step.net)      # before the diagnostics below run further steps
+    if args.dump_outputs:
+        _lib.set_deterministic(default_mode)                        # the diagnostics below measure the benchmark's own kernels
+        if rank == 0 and world == 1 and w["tgt"] is not None:
+            # one forward + backward of the default kernels from the state the timed steps left (no optimizer step, nothing timed):
+            # their outputs from one state differ between runs by float-atomic rounding only
+            l_d, t_d = step.forward_backward(w["tgt"])
+            torch.cuda.synchronize()
+            dump_outputs(args.dump_outputs, l_d, t_d, step.net, prefix="default_", params=False)
     facts = distributed_facts(world, dev, rccl_log)
     if world > 1:
         # every rank leaves the process group HERE, together: rank 0's single-rank diagnostics below (kernel replays, the fp32-MFMA
@@ -740,9 +804,10 @@ def main():
                                                                 if os.environ.get("DSF_CONV_MATH", "x6") == "x6" else ": fp32 MFMA"),
             "config": {"workload": w["workload"], "baseline_config": args.config, "unit_of_value": w["unit_note"],
                        "global_batch": B * world, "hip_graph": bool(args.graph), "init": args.init,
-                       "weight_gradients_on_second_stream": os.environ.get("DSF_WRW_STREAM", "1") != "0", "crop": 128, "raster": 640, "parallelism": "dp%d" % world,
+                       "weight_gradients_on_second_stream": os.environ.get("DSF_WRW_STREAM", "1") != "0" and not (args.graph and GRAPH_ONE_STREAM),
+                       "graph_captured_on_one_stream": bool(args.graph and GRAPH_ONE_STREAM), "crop": 128, "raster": 640, "parallelism": "dp%d" % world,
                        "mano_asset": "synthetic MANO-shaped hand (real MANO_RIGHT.pkl is license-gated)"},
-            "final_loss": round(loss_val, 5),
+            "final_loss": round(loss_val, 5), "deterministic": bool(args.dump_outputs) or default_mode,
             "distributed": facts,
         }
         out["roofline"], out["conv_kernels"], out["roofline_critical"] = conv_kernel_roofline(step, w["run_diag"])
